@@ -11,10 +11,16 @@ contiguously over the N ranks (strong scaling: 65 536 / N clips per GPU), follow
 all-gather of the (B/N, 12) logits.  Waveforms are resident in HBM before the timed region starts.  Rank 0 prints
 ONE JSON line.  `roofline` is for the dominant kernel (the fused res8 kernel, fp32-accurate three-term fp16 products on the
 matrix cores): algorithmic FLOPs per launch / its mean launch duration measured with HIP events on the launch stream
-inside the timed steps.  `cpu_baseline` (rank 0, N = 1 only) times the CPU oracle ("port": numpy/scipy rFFT front end +
-torch-CPU fp32 model, parity-pinned against the reference in tests/) on a bounded sample of the same clips, and `parity`
-compares the GPU logits of exactly those clips with the oracle's (tolerance 1e-3, argmax); the run exits non-zero
-when that check fails.  Inputs: SURVEY.md section 8d, except that the 1 kHz tone clips carry their clip's noise at
+inside the timed steps.  `--dump-outputs DIR` writes the last timed step's logits (gathered over the ranks for N > 1) to
+DIR/logits.npy (float32): the inputs are seeded, so two builds can be compared output for output.
+
+A plain run does only what the headline needs: set-up, pre-warm and warm-up, the K timed steps, the dump, the line.
+`--full` (N = 1) adds the records that take runs of their own: `cpu_baseline` times the CPU oracle ("port": numpy/scipy
+rFFT front end + torch-CPU fp32 model, parity-pinned against the reference in tests/) on a bounded sample of the same
+clips, and `parity` compares the GPU logits of exactly those clips with the oracle's (tolerance 1e-3, argmax); then the
+literal-tone parity, the 8 192-clip shard, the pinned-host (PCIe-inclusive) passes, the configs[1] / [2] / [4] records and
+the rocprofv3 traffic passes (each can be left out with its --no-* option).  A --full run exits non-zero when a parity
+check fails.  Inputs: SURVEY.md section 8d, except that the 1 kHz tone clips carry their clip's noise at
 -37 dB as dither (a bare bin-centred sine leaves every off-peak mel band pure rounding noise, on which no two fp32
 implementations -- the reference's included -- agree); the `data` field says so.
 """
@@ -509,10 +515,9 @@ def live_traffic(batch, kernel_substr="res8h_kernel", timeout_s=150):
         d = tempfile.mkdtemp(prefix="kws_pmc_", dir="/tmp")
         try:
             cmd = [exe, "--kernel-trace", "--pmc", ctr, "-d", d, "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__),
-                   "--steps", "2", "--warmup", "1", "--prewarm-ms", "0", "--batch", str(batch), "--no-cpu-baseline", "--no-secondary", "--no-shard",
-                   "--no-h2d", "--no-live-traffic"]
+                   "--steps", "2", "--warmup", "1", "--prewarm-ms", "0", "--batch", str(batch)]
             env = dict(os.environ, TMPDIR="/tmp")
-            for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "KWS_FORCE_DIST", "KWS_BENCH_DUMP"):
+            for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "KWS_FORCE_DIST"):
                 env.pop(k, None)
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s, cwd="/tmp", env=env)
             if r.returncode != 0:
@@ -579,11 +584,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--prewarm-ms", type=float, default=300.0, help="untimed load before the W warm-up steps (clock governor); 0 = none")
     ap.add_argument("--batch", type=int, default=65536, help="GLOBAL batch (clips per step over all GPUs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[2] / configs[4] records (N = 1 only)")
-    ap.add_argument("--no-shard", action="store_true", help="skip the 8 192-clip shard record (N = 1 only)")
-    ap.add_argument("--no-h2d", action="store_true", help="skip the pinned-host (PCIe-inclusive) record (N = 1 only)")
-    ap.add_argument("--no-live-traffic", action="store_true", help="do not re-run two short rocprofv3 --pmc passes of this command for roofline.traffic (N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's logits to DIR/logits.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="N = 1: after the headline, the CPU baseline with parity, the literal-tone parity, the shard, "
+                    "pinned-host and configs[1] / [2] / [4] records and the rocprofv3 traffic passes (a plain run does none of them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline, its parity and the literal-tone record")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the configs[1] / [2] / [4] records")
+    ap.add_argument("--no-shard", action="store_true", help="--full: skip the 8 192-clip shard record")
+    ap.add_argument("--no-h2d", action="store_true", help="--full: skip the pinned-host (PCIe-inclusive) record")
+    ap.add_argument("--no-live-traffic", action="store_true", help="--full: do not re-run two short rocprofv3 --pmc passes of this command for roofline.traffic")
     ap.add_argument("--allow-fallback", action="store_true", help="N > 1: if the side-stream all-gather is refused, gather on the compute stream instead of failing the run")
     args = ap.parse_args()
 
@@ -725,6 +733,12 @@ def main():
         if int(flag.item()):
             raise SystemExit(f"rank {rank}: the gathered logits differ from a rank's own shard")
 
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logits.npy"),
+                (gathered if (dist_on or self_gather) else logits).cpu().numpy().astype(np.float32))
+    full = world == 1 and args.full
     if rank == 0:
         clips_per_s = args.batch * args.steps / elapsed
         k_ms = model_ms / max(calls, 1)
@@ -769,7 +783,7 @@ def main():
                     continue
             # ... and measured in THIS run when rocprofv3 is here: two short child runs of this command under --pmc (after the timed region: they
             # cannot disturb it).  The committed figure stays beside it, so a traffic regression shows as a disagreement inside one line.
-            if world == 1 and not args.no_live_traffic:
+            if full and not args.no_live_traffic:
                 lt = live_traffic(args.batch)
                 if lt and "bytes" in lt:
                     roofline["traffic_static_committed"] = roofline.get("traffic")
@@ -808,7 +822,7 @@ def main():
                            "flop_frac_of_fp32_peak": clips_per_s / world * (F_ALG_MODEL + F_ALG_FRONTEND) / (PEAK_F32_MFMA_TFLOPS * 1e12)},
         }
         failed = False
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             # the CPU leg evaluates a time-bounded prefix of a sample that is spread over the WHOLE batch (every 4th clip, in an
             # order whose prefixes are spread too), and the parity check covers exactly those clips
             idx = torch.from_numpy(spread_indices(nloc, min(16384, nloc))).to(device)
@@ -816,30 +830,26 @@ def main():
             out["parity"] = parity_record(logits[idx[:len(want)]].cpu().numpy(), want)
             out["parity"]["clip_index_range"] = [int(idx[:len(want)].min()), int(idx[:len(want)].max())]
             failed = not out["parity"]["pass"]
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             try:
                 out["parity_literal_tone"] = literal_tone_record(torch, model, sd, device)
             except Exception as exc:                   # never let an extra record take the headline line down
                 out["parity_literal_tone"] = {"error": repr(exc)}
-        if world == 1 and not args.no_shard and args.batch >= 16384:
+        if full and not args.no_shard and args.batch >= 16384:
             out["shard"] = shard_record(torch, model, device, clips_per_s, k_ms, f_ms, nloc)
-        if world == 1 and not args.no_h2d:
+        if full and not args.no_h2d:
             try:
                 out["h2d_inclusive"] = h2d_record(torch, model, device, min(args.batch, 32768))
                 out["h2d_inclusive_pcm16"] = h2d_record(torch, model, device, min(args.batch, 32768), pcm16=True)
             except Exception as exc:
                 out["h2d_inclusive"] = {"error": repr(exc)}
-        if world == 1 and not args.no_secondary:
+        if full and not args.no_secondary:
             try:
                 out["secondary"] = secondary_configs(torch, device)
                 out["secondary"].append(config1_record(torch, model, sd, device, clips_per_s))
                 failed = failed or not all(r["parity"]["pass"] for r in out["secondary"])
             except Exception as exc:                   # never let an extra record take the headline line down
                 out["secondary"] = {"error": repr(exc)}
-        dump = os.environ.get("KWS_BENCH_DUMP")        # tests: the (gathered) logits of the last step, for comparison across N
-        if dump:
-            import numpy as np
-            np.save(dump, (gathered if (dist_on or self_gather) else logits).cpu().numpy())
         print(json.dumps(out))
         if failed:
             raise SystemExit("parity check failed: " + json.dumps({"headline": out.get("parity"), "secondary": [r.get("parity") for r in out.get("secondary", []) if isinstance(r, dict)]}))

@@ -33,6 +33,7 @@ def _free_port():
 
 def _worker(rank, world, port, total, out_dir):
     sys.path.insert(0, ROOT)
+    torch.cuda.is_available = lambda: False      # a CPU test of the gloo path: ranks stay off whatever GPUs the machine has
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     r, w = dist_utils.init_from_env("gloo")
@@ -96,6 +97,7 @@ def test_one_command_starts_its_own_ranks(tmp_path):
                 f"sys.path.insert(0, {ROOT!r})\n"
                 "from honk2_amd import dist_utils\n"
                 "import torch, torch.distributed as dist\n"
+                "torch.cuda.is_available = lambda: False\n"        # as in _worker: the ranks stay on the CPU
                 "r, w = dist_utils.init_from_env('gloo')\n"
                 "t = torch.tensor([r + 1.0]); dist.all_reduce(t)\n"
                 "open(os.path.join(sys.argv[1], f'rank{r}.txt'), 'w').write(f'{w} {t.item()} {os.environ[\"MASTER_ADDR\"]}')\n"

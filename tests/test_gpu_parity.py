@@ -1447,11 +1447,11 @@ def test_bench_two_ranks_rehearsal_matches_one_rank(torch_cuda, tmp_path):
     import socket
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     # `python bench.py --gpus 2` AS TYPED (no torchrun in front): the script starts its two ranks itself, as fresh children, and relays rank 0's line
-    env = dict(os.environ, KWS_BENCH_BACKEND="gloo", KWS_BENCH_ONE_DEVICE="1", KWS_BENCH_DUMP=str(tmp_path / "n2.npy"))
+    env = dict(os.environ, KWS_BENCH_BACKEND="gloo", KWS_BENCH_ONE_DEVICE="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     two = subprocess.run([sys.executable, os.path.join(root, "bench.py"),
-                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2048", "--prewarm-ms", "0"],
+                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2048", "--prewarm-ms", "0", "--dump-outputs", str(tmp_path / "n2")],
                          env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert two.returncode == 0, two.stderr[-2000:]
     lines2 = [ln for ln in two.stdout.splitlines() if ln.startswith("{")]
@@ -1474,29 +1474,29 @@ def test_bench_two_ranks_rehearsal_matches_one_rank(torch_cuda, tmp_path):
         port = sk.getsockname()[1]
     tr = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                          "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                         "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2048", "--prewarm-ms", "0"],
-                        env=dict(env, KWS_BENCH_DUMP=str(tmp_path / "n2t.npy")), capture_output=True, text=True, timeout=600, cwd=root)
+                         "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2048", "--prewarm-ms", "0", "--dump-outputs", str(tmp_path / "n2t")],
+                        env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert tr.returncode == 0, tr.stderr[-2000:]
-    assert np.array_equal(np.load(tmp_path / "n2t.npy"), np.load(tmp_path / "n2.npy"))
+    assert np.array_equal(np.load(tmp_path / "n2t" / "logits.npy"), np.load(tmp_path / "n2" / "logits.npy"))
     assert line2["steps"] == 2 and line2["warmup"] == 1 and line2["value"] > 0 and line2["scaling"] == "strong"
     assert "cpu_baseline" not in line2 and line2["roofline"]["launches"] == 2 and line2["prewarm"]["steps"] == 0
-    env1 = dict(os.environ, KWS_BENCH_DUMP=str(tmp_path / "n1.npy"))
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                          "--batch", "2048", "--no-cpu-baseline", "--no-secondary"], env=env1, capture_output=True, text=True, timeout=600, cwd=root)
+                          "--batch", "2048", "--dump-outputs", str(tmp_path / "n1")], capture_output=True, text=True, timeout=600, cwd=root)
     assert one.returncode == 0, one.stderr[-2000:]
     line1 = json.loads([ln for ln in one.stdout.splitlines() if ln.startswith("{")][-1])
     assert line1["n_gpus"] == 1 and line1["config"]["clips_per_gpu"] == 2048
     assert 0 < line1["prewarm"]["steps"] <= 400 and line1["roofline"]["launches"] == 2     # the untimed clock-governor pre-warm is not in the timed region
-    a, b = np.load(tmp_path / "n1.npy"), np.load(tmp_path / "n2.npy")
-    assert a.shape == b.shape == (2048, 12) and np.array_equal(a, b)
+    assert "cpu_baseline" not in line1 and "parity" not in line1 and "secondary" not in line1      # a plain run: the headline only
+    a, b = np.load(tmp_path / "n1" / "logits.npy"), np.load(tmp_path / "n2" / "logits.npy")
+    assert a.dtype == b.dtype == np.float32 and a.shape == b.shape == (2048, 12) and np.array_equal(a, b)
     # the RCCL leg gathers on a side stream while the next step computes (two buffers in rotation): the same stream / event logic
     # with a device copy standing in for the collective must hand back the last step's logits
-    env3 = dict(os.environ, KWS_BENCH_DUMP=str(tmp_path / "n1g.npy"), KWS_BENCH_SELF_GATHER="1")
+    env3 = dict(os.environ, KWS_BENCH_SELF_GATHER="1")
     for steps in ("2", "3"):
         sg = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", steps, "--warmup", "1",
-                             "--batch", "2048", "--no-cpu-baseline", "--no-secondary"], env=env3, capture_output=True, text=True, timeout=600, cwd=root)
+                             "--batch", "2048", "--dump-outputs", str(tmp_path / f"n1g{steps}")], env=env3, capture_output=True, text=True, timeout=600, cwd=root)
         assert sg.returncode == 0, sg.stderr[-2000:]
-        assert np.array_equal(np.load(tmp_path / "n1g.npy"), a)
+        assert np.array_equal(np.load(tmp_path / f"n1g{steps}" / "logits.npy"), a)
     # RCCL itself, on the hardware this box has: the distributed leg as a fresh torchrun child with a ONE-rank nccl process group
     # (KWS_FORCE_DIST): init_process_group("nccl"), the side-stream all_gather_into_tensor with its event hand-offs, barrier and the
     # MAX all-reduce of the step time all execute on RCCL; the gathered logits must be the local ones, via the overlapped path
@@ -1504,19 +1504,19 @@ def test_bench_two_ranks_rehearsal_matches_one_rank(torch_cuda, tmp_path):
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
-    env4 = dict(os.environ, KWS_FORCE_DIST="1", KWS_BENCH_DUMP=str(tmp_path / "n1r.npy"))
+    env4 = dict(os.environ, KWS_FORCE_DIST="1")
     env4.pop("KWS_BENCH_BACKEND", None)
     for steps in ("2", "3"):
         rc = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                              "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                             "--gpus", "1", "--steps", steps, "--warmup", "1", "--batch", "2048", "--no-cpu-baseline", "--no-secondary",
-                             "--no-shard", "--no-h2d"], env=env4, capture_output=True, text=True, timeout=600, cwd=root)
+                             "--gpus", "1", "--steps", steps, "--warmup", "1", "--batch", "2048", "--dump-outputs", str(tmp_path / f"n1r{steps}")],
+                            env=env4, capture_output=True, text=True, timeout=600, cwd=root)
         assert rc.returncode == 0, rc.stderr[-2000:]
         liner = json.loads([ln for ln in rc.stdout.splitlines() if ln.startswith("{")][-1])
         coll = liner["collective"]
         assert coll["backend"] == "nccl" and coll["world_size"] == 1 and coll["forced_one_rank_group"] and coll["rccl_version"]
         assert coll["overlapped_on_side_stream"] and coll["overlap_fallback"] is None, coll
-        assert np.array_equal(np.load(tmp_path / "n1r.npy"), a)
+        assert np.array_equal(np.load(tmp_path / f"n1r{steps}" / "logits.npy"), a)
 
 
 def test_entry_point_reduces_over_rccl_with_a_one_rank_group(torch_cuda, tmp_path):
